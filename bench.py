@@ -20,7 +20,11 @@ weak scaling (--batch instances per GPU); --total-batch T shards T instances ove
 --gpus 8 --total-batch 65536 = 8192 per GPU, "scaling": "strong").  value = instances solved by all ranks /
 max-over-ranks time.
 
-Rank 0 prints ONE JSON line with
+Rank 0 prints ONE JSON line: the headline (metric, value, unit, higher_is_better, dtype, ms_per_step) and the workload's
+config.  A plain run does only what that line needs: set-up, warm-up, the timed steps and, with --dump-outputs DIR, the
+solution record of the last timed step (x, y, z, obj, pri_res, dua_res, iter, status) as DIR/<name>.npy in float64 -- past
+64 MB a seeded sample of the instances, their indices in DIR/instance.npy.  --full adds what takes runs of its own or is
+not the headline:
   roofline        the kernel the north-star names: the batched permuted tri-solve (plugin `solve`), HBM-bound, timed live with
                   HIP events on its own stream over a rotation of handles (every launch streams from HBM) -- outside the timed
                   steps; roofline_resident = the same handle back to back (rows served by the Infinity Cache);
@@ -41,7 +45,9 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
+HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak
+DUMP_LIMIT = 64 << 20   # --dump-outputs: bytes at most; larger outputs are written as a seeded sample of the instances
+DUMP_KEYS = ("x", "y", "z", "obj", "pri_res", "dua_res", "iter", "status")   # the solution record of every instance
 N_CU, CLOCK_HZ = 256, 2.4e9
 PERTURB_POOL = 8        # distinct per-step perturbation draws kept on the device (cycled)
 
@@ -54,13 +60,18 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=4096, help="instances per GPU (weak scaling)")
     ap.add_argument("--total-batch", type=int, default=0, help="instances over ALL GPUs (strong scaling; config 4: 65536)")
     ap.add_argument("--iters", type=int, default=200, help="ADMM iterations per solve")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline, the tri-solve roofline (launches of its own) "
+                         "and the fused kernel's roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the arrays the last timed step computed to DIR/<name>.npy (float64, 64 MB at most)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--no-perturb", action="store_true", help="re-upload the same P / A values every step")
     ap.add_argument("--perturb-in-step", action="store_true",
                     help="form each step's perturbed P / A values inside the timed step (two elementwise kernels per step, as rounds "
                          "1-2 were timed) instead of cycling through value sets formed before the timed region")
     ap.add_argument("--sync-steps", action="store_true", help="blocking update_P_A / solve calls (host round trips inside a step)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: time budget of the CPU baseline")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the RCCL process group and run the result all-gather even with ONE rank (exercises the "
                          "collective path on a single GPU; the gather is then inside every timed step)")
@@ -261,7 +272,7 @@ def main(argv=None):
     if torch.cuda.device_count() == 0:                       # (does not initialise the GPU)
         raise SystemExit("bench.py needs a GPU: the backend has no CPU fallback")
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # timed BEFORE the GPU is initialised (host threads only, no fork).  Same workload, same permutation
         # (host-side symbolic analysis, no device needed).
         import osqp_recursive_ldl_amd as R0
@@ -292,9 +303,56 @@ def main(argv=None):
     dims = w.linsys().dims()
 
     elapsed, per_rank, res, gather_ms = run_steps(args, shard, n, m, sizes, scaling, world)
-    loops = shard.loops[-args.steps:] if args.sync_steps else shard.loops[-1:]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)             # what the last timed step computed, before anything else runs
 
     value = total * args.steps / elapsed
+    out = {
+        "metric": "QP solves/sec (batch) + ADMM iters/sec, n=50 m=100 fp64 batch=4096",
+        "value": value, "unit": "QP solves/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic", "timed_region_s": elapsed,
+        "admm_iters_per_sec": value * args.iters,
+        "config": {"workload": "random sparse QPs n=50 m=100 density=0.15, shared pattern, %d instances (%s), per step: P and A "
+                               "of every instance perturbed by 1 + 0.05 N(0,1)%s, numeric factor, %d ADMM iterations (rho=0.1 "
+                               "sigma=1e-6 alpha=1.6, adaptive_rho=0, check_termination=0, scaling=0)"
+                               % (total, "%d per GPU" % sizes[0] if len(set(sizes)) == 1 else "shards %s" % sizes,
+                                  " -- OFF (--no-perturb)" if args.no_perturb else
+                                  (" (products formed inside the step)" if args.perturb_in_step else
+                                   " (%d value sets formed before the timed region and resident in HBM, cycled: every step sees other "
+                                   "values than the step before)" % PERTURB_POOL), args.iters),
+                   "batch_total": total, "batch_per_gpu": sizes, "n": n, "m": m, "nnzKKT": dims["nnzKKT"], "nnzL": dims["nnzL"],
+                   "admm_iters": args.iters, "parallelism": "batch-sharded x%d, one all-gather of the result records per step" % world,
+                   "per_rank_seconds": per_rank, "gather_ms": gather_ms,
+                   "collective": ("RCCL all_gather_into_tensor of the result records inside every step, records packed by one launch, the exchange "
+                                  "asynchronous and double-buffered so the next step does not wait for it (backend %s, world %d%s)"
+                                  % (dist.get_backend(), world, ", --force-dist" if args.force_dist else "")) if coll else None},
+    }
+    status = res["status"]
+    out["config"]["status_counts"] = {str(int(k)): int((status == k).sum()) for k in torch.unique(status)}
+    if args.full:
+        out.update(roofline_figures(args, shard, wl, settings, dims, B, dev))
+
+    if cpu is not None:
+        assert np.array_equal(perm0, w.linsys().export_symbolic()["perm"])
+        out["cpu_baseline"] = cpu
+    sys.stdout.flush()
+    if rank == 0:
+        os.write(real_stdout, (json.dumps(out) + "\n").encode())
+    os.close(real_stdout)
+    w.cleanup()
+    if coll:
+        dist.destroy_process_group()
+
+
+def roofline_figures(args, shard, wl, settings, dims, B, dev):
+    """--full: the roofline of the plugin `solve` (launches of its own, after the timed steps) and of the fused iteration
+    kernel (from the timed steps' loop events and the committed PMC pass)."""
+    import numpy as np
+    import torch
+    import osqp_recursive_ldl_amd as R
+    w, n, m = shard.w, wl.n, wl.m
+    loops = shard.loops[-args.steps:] if args.sync_steps else shard.loops[-1:]
     N = n + m
     # algorithmic bytes per instance (SURVEY.md 8d): one tri-solve; one fused ADMM iteration = tri-solve + vector state
     tri_bytes = 8 * (dims["nnzL"] + 3 * N + m)
@@ -332,25 +390,6 @@ def main(argv=None):
             h.free()
     hbm_gbs = tri_bytes * B / (hbm_ms * 1e-3) / 1e9
     out = {
-        "metric": "QP solves/sec (batch) + ADMM iters/sec, n=50 m=100 fp64 batch=4096",
-        "value": value, "unit": "QP solves/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic", "timed_region_s": elapsed,
-        "admm_iters_per_sec": value * args.iters,
-        "config": {"workload": "random sparse QPs n=50 m=100 density=0.15, shared pattern, %d instances (%s), per step: P and A "
-                               "of every instance perturbed by 1 + 0.05 N(0,1)%s, numeric factor, %d ADMM iterations (rho=0.1 "
-                               "sigma=1e-6 alpha=1.6, adaptive_rho=0, check_termination=0, scaling=0)"
-                               % (total, "%d per GPU" % sizes[0] if len(set(sizes)) == 1 else "shards %s" % sizes,
-                                  " -- OFF (--no-perturb)" if args.no_perturb else
-                                  (" (products formed inside the step)" if args.perturb_in_step else
-                                   " (%d value sets formed before the timed region and resident in HBM, cycled: every step sees other "
-                                   "values than the step before)" % PERTURB_POOL), args.iters),
-                   "batch_total": total, "batch_per_gpu": sizes, "n": n, "m": m, "nnzKKT": dims["nnzKKT"], "nnzL": dims["nnzL"],
-                   "admm_iters": args.iters, "parallelism": "batch-sharded x%d, one all-gather of the result records per step" % world,
-                   "per_rank_seconds": per_rank, "gather_ms": gather_ms,
-                   "collective": ("RCCL all_gather_into_tensor of the result records inside every step, records packed by one launch, the exchange "
-                                  "asynchronous and double-buffered so the next step does not wait for it (backend %s, world %d%s)"
-                                  % (dist.get_backend(), world, ", --force-dist" if args.force_dist else "")) if coll else None},
         "roofline": {"bound": "hbm", "kernel": "batched permuted tri-solve + z~ epilogue (plugin `solve`: k_tile_solve3 on arrowhead "
                                                "patterns, else k_arrow_solve / k_plan_solve), rldl_batch_time_solve_rotating",
                      "achieved": hbm_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_gbs / HBM_PEAK_GBS, "traffic": None,
@@ -387,19 +426,23 @@ def main(argv=None):
     if tr and B == tr.get("batch") and tr.get("algorithmic_bytes_per_launch") == tri_bytes * B and "tile_solve3" in tr.get("kernel", ""):
         out["roofline"]["traffic"] = tr["traffic_bytes_per_launch"]
         out["roofline"]["traffic_source"] = "from_file: profiles/r3_pmc_traffic_solve.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes)"
-    status = res["status"]
-    out["config"]["status_counts"] = {str(int(k)): int((status == k).sum()) for k in torch.unique(status)}
+    return out
 
-    if cpu is not None:
-        assert np.array_equal(perm0, w.linsys().export_symbolic()["perm"])
-        out["cpu_baseline"] = cpu
-    sys.stdout.flush()
-    if rank == 0:
-        os.write(real_stdout, (json.dumps(out) + "\n").encode())
-    os.close(real_stdout)
-    w.cleanup()
-    if coll:
-        dist.destroy_process_group()
+
+def dump_outputs(path, res):
+    """--dump-outputs: the solution record of the last timed step as path/<name>.npy, float64.  Past DUMP_LIMIT bytes, a sample
+    of the instances drawn with a fixed seed (the same rows for the same arguments), their indices in path/instance.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {k: res[k].detach().cpu().numpy().astype(np.float64) for k in DUMP_KEYS if k in res}
+    rows = arrs["x"].shape[0]
+    per_row = sum(a[:1].nbytes for a in arrs.values())
+    if per_row * rows > DUMP_LIMIT:                          # (+ 8 bytes per row of instance.npy, 4 KB for the .npy headers)
+        keep = np.sort(np.random.default_rng(0).choice(rows, (DUMP_LIMIT - 4096) // (per_row + 8), replace=False))
+        arrs = {k: a[keep] for k, a in arrs.items()}
+        arrs["instance"] = keep.astype(np.float64)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def load_profile(name):

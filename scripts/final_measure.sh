@@ -18,9 +18,9 @@ timeout -k 10 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INST
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/m3 -- python3 scripts/pmc_run_mpc.py > $O/m3.log 2>&1 &&
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/m4 -- python3 scripts/pmc_run_mpc.py > $O/m4.log 2>&1 &&
 python3 scripts/pmc_reduce.py mpc $O/pmc_mpc.json $O/m1 $O/m2 $O/m3 $O/m4 > /dev/null &&
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline > $O/stats.log 2>&1 &&
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $O/stats.log 2>&1 &&
 cp $O/stats/*/*kernel_stats.csv $O/kernel_stats.csv &&
-timeout -k 10 600 python3 bench.py > $O/bench.log 2>&1 && tail -1 $O/bench.log > $O/bench.json &&
+timeout -k 10 600 python3 bench.py --full > $O/bench.log 2>&1 && tail -1 $O/bench.log > $O/bench.json &&
 timeout -k 10 600 python3 scripts/bench_configs.py all > $O/configs.log 2>&1 && grep '^{' $O/configs.log > $O/configs.jsonl &&
 timeout -k 10 300 python3 scripts/solve_probe.py --batches 1024,4096,8192 --json $O/solve_timeline.json > $O/solve_probe.log 2>&1 &&
 timeout -k 10 300 python3 scripts/factor_bench.py 64 1024 4096 > $O/factor_timeline.txt 2>&1
